@@ -9,6 +9,12 @@ output samples of all ranks / max-over-ranks wall time.
 
   python bench.py --gpus N --steps K --warmup W
   torchrun --nproc-per-node N ... bench.py --gpus N ...     (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the result line (the headline
+figure and the per-kernel event times of the last step).  --dump-outputs DIR also writes
+what the last timed step left on the device (dump_outputs).  --full adds the legs that take
+runs of their own after the timed steps: the end-to-end .dat path, single-pulse search,
+FFT rows, rfifind, PSRFITS streaming and the two CPU baselines.
 """
 import argparse
 import glob
@@ -35,7 +41,13 @@ def parse():
     ap.add_argument("--nbits", type=int, default=8)
     ap.add_argument("--variant", type=int, default=0,
                     help="hd_plan_set_variant value for every plan (0 auto; probe bits are for profiling only)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU-baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs with runs of their own (--e2e-beams, --sp-beams, "
+                         "--fft-beams, --rfi-beams, --stream-beams) and the CPU baselines; off: the timed steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed (a fixed sample of every DM's "
+                         "series and every DM's exact sum, see dump_outputs) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU-baseline leg")
     ap.add_argument("--streams", type=int, default=1, choices=(1, 2, 3),
                     help="stage-2 HIP streams (hd_set_streams): 2 overlaps consecutive passes (no launch tails), 3 runs "
                          "stage 2 on its own stream so the next DDplan stage's stage 1 overlaps it; per-kernel event "
@@ -47,9 +59,9 @@ def parse():
                     help="stage 1 as one hd_run_subband_multi call per DDplan stage instead of one for every "
                          "stage with ds >= 2 (the fused k_stage1_q8m launch)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU work for the baseline sample")
-    # the legs after the timed steps characterise one GPU: by default (-1) they run at world
-    # size 1 only (8 ranks each writing a beam's 47 GB of .dat files, or two 4 GB PSRFITS
-    # beams, would share one host's tmpfs)
+    # the legs after the timed steps (--full only) characterise one GPU: by default (-1) they
+    # run at world size 1 only (8 ranks each writing a beam's 47 GB of .dat files, or two 4 GB
+    # PSRFITS beams, would share one host's tmpfs)
     ap.add_argument("--e2e-beams", type=int, default=-1,
                     help="beams run end to end (.dat/.inf files written) after the timed steps; 0 = skip")
     ap.add_argument("--sp-beams", type=int, default=-1,
@@ -86,7 +98,46 @@ def parse():
                     help="--mode slices on ONE process: run only rank R's slice of a G-way cut (no collectives; the "
                          "other ranks' clip statistics are absent, so only the timing is meaningful) -- the per-rank "
                          "compute time behind the multi-GPU prediction, not a scaling measurement")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        for leg in LEGS:
+            if getattr(args, leg) > 0:
+                ap.error("--%s runs a leg after the timed steps: add --full" % leg.replace("_", "-"))
+    return args
+
+
+# legs after the timed steps and the beams each runs by default (--full, world size 1)
+LEGS = {"e2e_beams": 1, "sp_beams": 1, "fft_beams": 1, "rfi_beams": 1, "stream_beams": 3}
+DUMP_WINDOW = 1024         # --dump-outputs: samples per window, three windows per DM
+
+
+def dump_outputs(outdir, plans, rank, world):
+    """--dump-outputs: what the timed path left for its caller in the last step, i.e. every
+    pass's per-DM series in HBM.  A beam's 4188 series hold 47 GB, so the files carry
+      series_sums.npy     float64 [DMs]: hd_series_sum (exact) of all numout samples of every DM,
+                          passes in plan order -- every output sample counts in one of them;
+      series_windows.npy  float32, per pass in plan order [numdms][3][w] flattened: samples
+                          [s, s + w) of every DM for s = 0, one seeded start, numout - w (the
+                          padded tail), w = min(DUMP_WINDOW, numout);
+      series_index.npy    float64 [passes][6]: numdms, numout, w and the three starts.
+    The starts come from a fixed seed and the plan geometry alone, so two builds run with the
+    same arguments write the same samples (51 MB for the default beam).  At world size > 1
+    every rank writes its own files, named <name>_rank<k>.npy."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    rng = np.random.default_rng(0x5eed)
+    sums, wins, index = [], [], []
+    for p in plans:
+        n, nd = int(p.numout), p.pp.numdms
+        w = min(DUMP_WINDOW, n)
+        starts = [0, int(rng.integers(0, n - w + 1)), n - w]
+        wins.append(np.stack([p.get_series(0, nd, s, w) for s in starts], axis=1).ravel())
+        sums.append(np.array([p.series_sum(d, 0, n) for d in range(nd)], np.float64))
+        index.append([nd, n, w] + starts)
+    tag = "" if world == 1 else "_rank%d" % rank
+    for name, arr in (("series_sums", np.concatenate(sums)), ("series_windows", np.concatenate(wins)),
+                      ("series_index", np.array(index, np.float64))):
+        np.save(os.path.join(outdir, name + tag + ".npy"), arr)
 
 
 def dist_setup(args):
@@ -608,6 +659,8 @@ def pointing_main(args, world, rank, local, dist, torch):
                            "slice timings (a prediction, not a measurement)"
                            % (S.POINTING_FIXED_MS, S.POINTING_BEAM_MS),
     }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [p for _, _, _, pl in work for p in pl], rank, world)
     if args.check_union:
         mine_ck = {(b, sl): slice_checksums(ts, sl, [pl]) for b, sl, _, pl in work}
         gathered = [None] * world
@@ -651,9 +704,9 @@ def main():
     DD_MULTI = not args.dd_single
     S1_FUSE = not args.s1_per_stage
     world, rank, local, dist, torch = dist_setup(args)
-    for leg, n1 in (("e2e_beams", 1), ("sp_beams", 1), ("fft_beams", 1), ("rfi_beams", 1), ("stream_beams", 3)):
+    for leg, n1 in LEGS.items():
         if getattr(args, leg) < 0:
-            setattr(args, leg, n1 if world == 1 else 0)
+            setattr(args, leg, n1 if args.full and world == 1 else 0)
     from hipdedisp import Engine, Opts, plan as P
     from hipdedisp.synth import palfa_obs, palfa_synth, rfifind_ptsperint, synth_mask
 
@@ -828,6 +881,8 @@ def main():
     }
     if shard:
         line["broadcast_ms_per_step"] = 1e3 * bcast_s / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, plans, rank, world)
     if not (shard or slices) and args.e2e_beams > 0:
         out_bytes = 4 * sum(p.pp.numdms * p.numout for p in plans)
         outdir = e2e_dir(1.1 * max(4 * p.pp.numdms * p.numout for p in plans) * 30)
@@ -869,7 +924,7 @@ def main():
             eng.close()
             line["union_check"] = union_check(lambda: Engine(local), obs, synth, ddplans, mask, pts, pad, gathered)
         barrier(dist, torch)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline(obs, synth, ddplans, args.cpu_seconds, mask, pts, pad, omp=False)
         line["cpu_baseline_openmp"] = cpu_baseline(obs, synth, ddplans, args.cpu_seconds, mask, pts, pad, omp=True)
     if rank == 0:

@@ -9,7 +9,7 @@ i=0
 for e in "$@"; do
   i=$((i + 1))
   d=gpurun_out/absp_$i
-  env $e timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $d -o run -- python3 bench.py --steps 1 --warmup 1 \
+  env $e timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $d -o run -- python3 bench.py --full --steps 1 --warmup 1 \
       --no-cpu --e2e-beams 0 --sp-beams 1 --fft-beams 0 --rfi-beams 0 --stream-beams 0 > $d.log 2>&1 \
       || { echo "setting [$e] failed"; exit 1; }
   python3 scripts/kstats.py "$(find $d -name '*.db' | head -1)" $d.csv

@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 rm -rf gpurun_out/pmcsp && mkdir -p gpurun_out/pmcsp
-B="python3 bench.py --steps 1 --warmup 0 --no-cpu --e2e-beams 0 --sp-beams 1 --fft-beams 0 --rfi-beams 0 --stream-beams 0"
+B="python3 bench.py --full --steps 1 --warmup 0 --no-cpu --e2e-beams 0 --sp-beams 1 --fft-beams 0 --rfi-beams 0 --stream-beams 0"
 run() {  # name counters...
   local n=$1; shift
   timeout -s KILL 240 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/pmcsp/$n -o $n --pmc "$@" -- $B \
