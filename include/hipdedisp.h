@@ -525,6 +525,76 @@ HD_API int hd_rednoise_blocks(int64_t numbins, double T, int32_t startwidth, int
 HD_API int hd_rednoise(hd_plan* plan, int32_t startwidth, int32_t endwidth, double endfreq, double T);
 /* Spectra of DM series dm0 .. dm0 + ndm - 1: out[ndm][numout] floats (numout/2 complex).  */
 HD_API int hd_get_fft(hd_plan* plan, int32_t dm0, int32_t ndm, float* out);
+/* The inverse of hd_get_fft: in[ndm][numout] floats (packed spectra) into DM rows dm0 ..
+ * dm0 + ndm - 1 of the plan's spectra buffer, which is built as hd_fft_prepare does when the
+ * geometry is new and taken over as hd_realfft does (the plan need not have run; rows outside
+ * the range keep what the buffer held).  For a caller that already holds .fft files, and for
+ * searching crafted spectra.                                                              */
+HD_API int hd_set_fft(hd_plan* plan, int32_t dm0, int32_t ndm, const float* in);
+
+/* ---- zero-acceleration harmonic-sum search on the device-resident spectra --------------
+ * Replaces the per-.fft `accelsearch -zmax 0 -numharm 16 -sigma 2.0 -flo 2.0 <fft>` of
+ * lib/python/PALFA2_presto_search.py:560-568 (lo_accel_*: lib/python/config/
+ * searching_example.py:20-23) [PRESTO-ext, restated; parity with PRESTO unpinned] on the
+ * plan's spectra after hd_rednoise (noise power about 1; F[0] and bins outside [1, nb),
+ * nb = numout/2, read as 0):
+ *   (a) half-bin power plane P[0 .. 2 nb), float32: P[2k] = |F[k]|^2; P[2k+1] = the power of
+ *       the Fourier interpolation at k + 1/2 over 16 taps a side, t_j = (float)(1 / (pi (j -
+ *       1/2))), per component acc = acc + t_j * (F[k+j] - F[k+1-j]) for j = 1 .. 16 in float32
+ *       without fused multiply-adds; powers are (float)((double)re^2 + (double)im^2);
+ *       P[0] = P[1] = 0;
+ *   (b) harmonic sums at r2, the top harmonic's frequency in half bins, for the stages H = 1,
+ *       2, 4, 8, 16 up to numharm: fraction h/H of r2 lies at floor((2 r2 h + H) / (2 H)); a
+ *       float32 add chain S = P[r2], + 1/2, + 1/4 + 3/4, + odd eighths, + odd sixteenths
+ *       (ascending), its value after each stage being that stage's summed power; r2 runs over
+ *       [2 rlo, 2 rhi], rlo = max(1, floor(flo T)), rhi = min(floor(fhi T), nb - 1); a
+ *       candidate's fundamental is r2 / (2 H) bins;
+ *   (c) powcut_H: log Q(H, powcut) = log sf_normal(sigma) - log numindep_H, Q(H, P) = e^-P
+ *       sum_{k<H} P^k / k!, numindep_H = (rhi - rlo) / H; the device compares S >
+ *       (float)powcut_H;
+ *   (d) per (DM, H) and aligned block of 64 half bins (r2 >> 6) the largest S above the
+ *       threshold is a hit (ties: the lowest r2);
+ *   (e) hd_accel_prune, a deterministic stand-in for accelsearch's ACCEL_CLOSEST_R merge;
+ *   (f) a hit's sigma: log p = min(0, log Q(H, power) + log numindep_H), sigma = -Phi^-1(p)
+ *       evaluated in log space, 0 when p >= 0.5.
+ * Not covered: -zmax 50, candidate optimisation and -harmpolish, accelsearch's own
+ * block-median normalisation, the _ACCEL_0 / .cand / .txtcand files, sifting.
+ * Memory: the P plane (numdms * numout * 4 bytes, as large as the spectra) is one buffer of
+ * the context, grown to the largest geometry searched and reused by every plan; the search
+ * is synchronous, so plans never share it in flight.                                      */
+typedef struct {
+    int32_t dm;        /* DM index in the plan                                           */
+    int32_t numharm;   /* harmonics summed: 1, 2, 4, 8 or 16                             */
+    int32_t r2;        /* top harmonic's frequency in half bins; fundamental r2/(2 numharm) */
+    float   power;     /* the stage's summed power                                       */
+    double  sigma;     /* (f)                                                            */
+} hd_acc_hit;
+/* The 16 interpolation taps of (a).  Host only.                                          */
+HD_API int hd_accel_taps(float* taps16);
+/* (c) and (f) for one stage (numharm 1 .. 16, numindep > 0).  Host only.                 */
+HD_API int hd_accel_powcut(double sigma, int32_t numharm, double numindep, double* power);
+HD_API int hd_accel_sigma(double power, int32_t numharm, double numindep, double* sigma);
+/* (a)-(d) on the plan's current spectra (T = numout * dt seconds), then (f): hits[cap]
+ * sorted by (dm, numharm, r2), *nhits the count; when the hits exceed cap nothing is copied,
+ * *nhits is that number and HD_E_NOMEM is returned (call again with room).  powcut5[5] (may
+ * be NULL) receives powcut of the stages searched (0 for the others).  HD_E_STATE: the plan
+ * holds no spectra or another plan took the buffer over; HD_E_INVAL: numharm not one of 1, 2,
+ * 4, 8, 16, or rlo >= rhi; HD_E_HIP on an HD_HOST_ONLY context.                            */
+HD_API int hd_accel_search(hd_plan* plan, double T, double flo, double fhi, int32_t numharm, double sigma,
+                           hd_acc_hit* hits, int64_t cap, int64_t* nhits, double* powcut5);
+/* P[q0 .. q0 + count) of DM dm of the plan's last hd_accel_search (HD_E_STATE when the plane
+ * holds another search), for cross-checks.                                                */
+HD_API int hd_accel_get_powers(hd_plan* plan, int32_t dm, int64_t q0, int64_t count, float* out);
+/* Device time of the two kernels of the plan's last hd_accel_search, ms: the power plane, and
+ * the harmonic sums with the hit-count memset before them (the last run when the device hit
+ * list had to grow).  Either may be NULL.                                                  */
+HD_API int hd_accel_last_ms(const hd_plan* plan, float* ms_powers, float* ms_sums);
+/* (e) on caller-supplied hits (any order, n of them): per DM in descending sigma (ties: the
+ * lower numharm, then the lower r2) a hit is kept unless an already kept one's fundamental
+ * lies within closest_r bins (|difference| < closest_r; accelsearch's 15.0).  The kept hits
+ * are compacted to the front, DMs ascending, each DM's in that order; *nkept of them.  Host
+ * only.                                                                                   */
+HD_API int hd_accel_prune(hd_acc_hit* hits, int64_t n, double closest_r, int64_t* nkept);
 
 #ifdef __cplusplus
 }

@@ -160,6 +160,19 @@ struct hd_ctx {
     // buffer, shared by the plans of that geometry -- each pass's hd_realfft takes it over
     // (the owner), so a beam builds 6 hipFFT plans, not 57
     std::map<std::tuple<int64_t, int, int64_t>, hd::FftState*> fft_cache;
+    // harmonic-sum search (hd_accel_search): the half-bin power plane [acc_ndm][2 acc_nb] of
+    // the last search (acc_owner: its plan), the device hit list and its counter; all grow to
+    // the largest search and are reused (the search is synchronous)
+    float* d_accP = nullptr;
+    size_t accP_cap = 0;               // floats
+    const void* acc_owner = nullptr;
+    int64_t acc_nb = 0;
+    int32_t acc_ndm = 0;
+    hd_acc_hit* d_acc_hits = nullptr;
+    int64_t acc_hits_cap = 0;
+    unsigned long long* d_acc_count = nullptr;
+    hipEvent_t acc_ev[3] = {nullptr, nullptr, nullptr};   // before / between / after its two kernels
+    float acc_ms[2] = {0.0f, 0.0f};
     // overlapped ingest of the next beam (hd_prefetch_*, hd_swap_raw): a second raw slot filled
     // by a reader thread through its own pinned blocks on its own copy stream
     struct Prefetch;
@@ -589,6 +602,11 @@ extern "C" int hd_close(hd_ctx* c)
     clear_special_cache(c);
     for (auto& kv : c->fft_cache) hd::fft_state_free(kv.second);
     c->fft_cache.clear();
+    dfree(c->d_accP);
+    dfree(c->d_acc_hits);
+    dfree(c->d_acc_count);
+    for (hipEvent_t e : c->acc_ev)
+        if (e) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
     delete c;
     return HD_OK;
@@ -1537,6 +1555,7 @@ static void plan_free(hd_plan* p)
     dfree(p->d_padv);
     if (p->fft && hd::fft_owner(p->fft) == p) hd::fft_set_owner(p->fft, nullptr);   // the context owns it
     p->fft = nullptr;
+    if (p->ctx->acc_owner == p) p->ctx->acc_owner = nullptr;
     for (auto& e : p->ev)
         if (e) (void)hipEventDestroy(e);
     p->dd_cur.reset();
@@ -2301,6 +2320,7 @@ extern "C" int hd_plan_destroy(hd_plan* p)
         if (p->dd_cur) p->dd_cur->e[0] = p->dd_cur->e[1] = nullptr;
         delete p->sp;                 // (its buffer set belongs to the context's sp_all)
         if (p->fft && hd::fft_owner(p->fft) == p) hd::fft_set_owner(p->fft, nullptr);
+        if (c->acc_owner == p) c->acc_owner = nullptr;
         delete p;
         if (!c->faulted) return HD_OK;
         return fail(c, HD_E_HIP, "hd_plan_destroy: the device faulted earlier (%s); device memory is left to the process exit",
@@ -4663,6 +4683,192 @@ extern "C" int hd_get_fft(hd_plan* p, int32_t dm0, int32_t ndm, float* out)
     HIPCHK(c, d2h_2d(out, sizeof(float) * p->numout, hd::fft_buffer(p->fft) + (size_t)dm0 * fs,
                      sizeof(float2) * fs, sizeof(float) * p->numout, ndm, st));
     HIPCHK(c, hd::fft_end(p->fft, st));
+    return HD_OK;
+}
+
+extern "C" int hd_set_fft(hd_plan* p, int32_t dm0, int32_t ndm, const float* in)
+{
+    if (!p || !in) return fail(p ? p->ctx : nullptr, HD_E_INVAL, "hd_set_fft: NULL argument");
+    hd_ctx* c = p->ctx;
+    if (p->numout < 4 || p->numout % 2) return fail(c, HD_E_INVAL, "hd_set_fft: numout %lld must be even, >= 4",
+                                                    (long long)p->numout);
+    if (p->out_stride > INT32_MAX) return fail(c, HD_E_INVAL, "hd_set_fft: series stride beyond 2^31");
+    if (dm0 < 0 || ndm < 1 || dm0 + ndm > p->pass.numdms) return fail(c, HD_E_INVAL, "hd_set_fft: bad DM range");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = p->dd_stream ? p->dd_stream : c->stream;
+    const auto key = std::make_tuple(p->numout, p->pass.numdms, p->out_stride);
+    hd::FftState*& st_fft = c->fft_cache[key];
+    if (!st_fft) st_fft = hd::fft_state_new();
+    HIPCHK(c, hd::fft_prepare(st_fft, p->out_stride, p->numout, p->pass.numdms));
+    p->fft = st_fft;
+    hd::fft_set_owner(p->fft, nullptr);            // (a failed copy leaves no owner)
+    const int64_t fs = p->numout / 2 + 1;
+    HIPCHK(c, hd::fft_begin(p->fft, st));          // after the last op on the shared spectra
+    HIPCHK(c, hipStreamSynchronize(st));           // `in` is the caller's (pageable) memory
+    HIPCHK(c, hipMemcpy2D(hd::fft_buffer(p->fft) + (size_t)dm0 * fs, sizeof(float2) * fs, in, sizeof(float) * p->numout,
+                          sizeof(float) * p->numout, ndm, hipMemcpyHostToDevice));
+    HIPCHK(c, hd::fft_end(p->fft, st));
+    hd::fft_set_owner(p->fft, p);
+    p->ran_fft = true;
+    return HD_OK;
+}
+
+// ---- zero-acceleration harmonic-sum search (hd_accel.hip; replaces the per-.fft
+//      `accelsearch -zmax 0` of PALFA2_presto_search.py:560-568) -----------------------------
+static int acc_stage_of(int32_t numharm)
+{
+    for (int s = 0; s < 5; s++)
+        if (numharm == (1 << s)) return s;
+    return -1;
+}
+
+extern "C" int hd_accel_taps(float* taps16)
+{
+    if (!taps16) return fail(nullptr, HD_E_INVAL, "hd_accel_taps: NULL argument");
+    hd::accel_taps(taps16);
+    return HD_OK;
+}
+
+extern "C" int hd_accel_powcut(double sigma, int32_t numharm, double numindep, double* power)
+{
+    if (!power || numharm < 1 || numharm > 16 || !std::isfinite(sigma) || !(numindep > 0.0) || !std::isfinite(numindep))
+        return fail(nullptr, HD_E_INVAL, "hd_accel_powcut: bad argument");
+    *power = hd::accel_powcut(sigma, numharm, numindep);
+    return HD_OK;
+}
+
+extern "C" int hd_accel_sigma(double power, int32_t numharm, double numindep, double* sigma)
+{
+    if (!sigma || numharm < 1 || numharm > 16 || std::isnan(power) || !(numindep > 0.0) || !std::isfinite(numindep))
+        return fail(nullptr, HD_E_INVAL, "hd_accel_sigma: bad argument");
+    *sigma = hd::accel_sigma(power, numharm, numindep);
+    return HD_OK;
+}
+
+extern "C" int hd_accel_prune(hd_acc_hit* hits, int64_t n, double closest_r, int64_t* nkept)
+{
+    if (!nkept || n < 0 || (n > 0 && !hits) || std::isnan(closest_r))
+        return fail(nullptr, HD_E_INVAL, "hd_accel_prune: bad argument");
+    *nkept = hd::accel_prune(hits, n, closest_r);
+    return HD_OK;
+}
+
+extern "C" int hd_accel_search(hd_plan* p, double T, double flo, double fhi, int32_t numharm, double sigma,
+                               hd_acc_hit* hits, int64_t cap, int64_t* nhits, double* powcut5)
+{
+    if (!p || !nhits || cap < 0 || (cap > 0 && !hits))
+        return fail(p ? p->ctx : nullptr, HD_E_INVAL, "hd_accel_search: bad argument");
+    hd_ctx* c = p->ctx;
+    const int smax = acc_stage_of(numharm);
+    if (smax < 0) return fail(c, HD_E_INVAL, "hd_accel_search: numharm %d is not 1, 2, 4, 8 or 16", numharm);
+    if (!(T > 0.0) || !std::isfinite(T) || !(flo >= 0.0) || !(fhi > 0.0) || !std::isfinite(flo) || !std::isfinite(fhi) ||
+        !std::isfinite(sigma))
+        return fail(c, HD_E_INVAL, "hd_accel_search: bad T, flo, fhi or sigma");
+    if (c->device == HD_HOST_ONLY) return fail(c, HD_E_HIP, "hd_accel_search: the context has no device");
+    if (!p->ran_fft) return fail(c, HD_E_STATE, "hd_accel_search: the plan holds no spectra (hd_realfft / hd_set_fft first)");
+    if (hd::fft_owner(p->fft) != p)
+        return fail(c, HD_E_STATE, "hd_accel_search: the spectra were replaced by another plan's hd_realfft (same geometry)");
+    const int64_t nb = p->numout / 2;
+    const int ndm = p->pass.numdms;
+    if (nb > ((int64_t)1 << 29)) return fail(c, HD_E_INVAL, "hd_accel_search: spectrum beyond 2^29 bins");
+    const double dlo = std::floor(flo * T), dhi = std::floor(fhi * T);
+    const int64_t rlo = dlo < 1.0 ? 1 : (dlo >= (double)nb ? nb : (int64_t)dlo);
+    const int64_t rhi = dhi >= (double)(nb - 1) ? nb - 1 : (dhi < 0.0 ? 0 : (int64_t)dhi);
+    if (rlo >= rhi)
+        return fail(c, HD_E_INVAL, "hd_accel_search: empty search range (rlo %lld >= rhi %lld)", (long long)rlo,
+                    (long long)rhi);
+    const int nstage = smax + 1;
+    double numindep[5] = {0, 0, 0, 0, 0}, pc[5] = {0, 0, 0, 0, 0};
+    float cut[5] = {0, 0, 0, 0, 0};
+    for (int s = 0; s < nstage; s++) {
+        numindep[s] = (double)(rhi - rlo) / (double)(1 << s);
+        pc[s] = hd::accel_powcut(sigma, 1 << s, numindep[s]);
+        cut[s] = (float)pc[s];
+    }
+    if (powcut5)
+        for (int s = 0; s < 5; s++) powcut5[s] = pc[s];
+    float taps[16];
+    hd::accel_taps(taps);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = p->dd_stream ? p->dd_stream : c->stream;
+    const int64_t pstride = 2 * nb;
+    const size_t pneed = (size_t)pstride * ndm;
+    c->acc_owner = nullptr;                                  // (a failed search leaves no plane)
+    if (c->accP_cap < pneed) {
+        HIPCHK(c, sync_all(c));
+        dfree(c->d_accP);
+        c->d_accP = nullptr;
+        c->accP_cap = 0;
+        HIPCHK(c, hipMalloc(&c->d_accP, sizeof(float) * pneed));
+        c->accP_cap = pneed;
+    }
+    if (!c->d_acc_count) HIPCHK(c, hipMalloc(&c->d_acc_count, sizeof(unsigned long long)));
+    if (!c->d_acc_hits) {
+        HIPCHK(c, hipMalloc(&c->d_acc_hits, sizeof(hd_acc_hit) * ((size_t)1 << 12)));   // (a pass at sigma 2: tens)
+        c->acc_hits_cap = (int64_t)1 << 12;
+    }
+    for (hipEvent_t& e : c->acc_ev)
+        if (!e) HIPCHK(c, hipEventCreate(&e));
+    const int64_t fs = nb + 1;
+    unsigned long long cnt = 0;
+    HIPCHK(c, hd::fft_begin(p->fft, st));          // after the last op on the shared spectra
+    HIPCHK(c, hipEventRecord(c->acc_ev[0], st));
+    HIPCHK(c, hd::launch_acc_powers(hd::fft_buffer(p->fft), fs, nb, ndm, taps, c->d_accP, pstride, st));
+    HIPCHK(c, hd::fft_end(p->fft, st));
+    for (int pass = 0; pass < 2; pass++) {
+        HIPCHK(c, hipMemsetAsync(c->d_acc_count, 0, sizeof(unsigned long long), st));
+        HIPCHK(c, hipEventRecord(c->acc_ev[1], st));
+        HIPCHK(c, hd::launch_acc_harm(c->d_accP, pstride, ndm, 2 * rlo, 2 * rhi, nstage, cut, c->d_acc_hits,
+                                      c->d_acc_count, c->acc_hits_cap, st));
+        HIPCHK(c, hipEventRecord(c->acc_ev[2], st));
+        HIPCHK(c, d2h(&cnt, c->d_acc_count, sizeof cnt, st));
+        if ((int64_t)cnt <= c->acc_hits_cap) break;
+        // the device list overflowed: grow it to the count and run the sums again
+        const int64_t ncap = (int64_t)cnt + (int64_t)cnt / 4;
+        dfree(c->d_acc_hits);
+        c->d_acc_hits = nullptr;
+        c->acc_hits_cap = 0;
+        HIPCHK(c, hipMalloc(&c->d_acc_hits, sizeof(hd_acc_hit) * (size_t)ncap));
+        c->acc_hits_cap = ncap;
+    }
+    HIPCHK(c, hipEventElapsedTime(&c->acc_ms[0], c->acc_ev[0], c->acc_ev[1]));
+    HIPCHK(c, hipEventElapsedTime(&c->acc_ms[1], c->acc_ev[1], c->acc_ev[2]));
+    c->acc_owner = p;
+    c->acc_nb = nb;
+    c->acc_ndm = ndm;
+    *nhits = (int64_t)cnt;
+    if ((int64_t)cnt > cap)
+        return fail(c, HD_E_NOMEM, "hd_accel_search: %llu hits > capacity %lld (call again with room)", cnt,
+                    (long long)cap);
+    if (!cnt) return HD_OK;
+    HIPCHK(c, d2h(hits, c->d_acc_hits, sizeof(hd_acc_hit) * cnt, st));
+    hd::accel_sort(hits, (int64_t)cnt);
+    for (unsigned long long i = 0; i < cnt; i++)
+        hits[i].sigma = hd::accel_sigma((double)hits[i].power, hits[i].numharm, numindep[acc_stage_of(hits[i].numharm)]);
+    return HD_OK;
+}
+
+extern "C" int hd_accel_get_powers(hd_plan* p, int32_t dm, int64_t q0, int64_t count, float* out)
+{
+    if (!p || !out) return fail(p ? p->ctx : nullptr, HD_E_INVAL, "hd_accel_get_powers: NULL argument");
+    hd_ctx* c = p->ctx;
+    if (c->acc_owner != p || !c->d_accP)
+        return fail(c, HD_E_STATE, "hd_accel_get_powers: the power plane does not hold this plan's search");
+    if (dm < 0 || dm >= c->acc_ndm || q0 < 0 || count < 0 || q0 + count > 2 * c->acc_nb)
+        return fail(c, HD_E_INVAL, "hd_accel_get_powers: bad range");
+    if (!count) return HD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = p->dd_stream ? p->dd_stream : c->stream;
+    HIPCHK(c, d2h(out, c->d_accP + (size_t)dm * 2 * (size_t)c->acc_nb + (size_t)q0, sizeof(float) * (size_t)count, st));
+    return HD_OK;
+}
+
+extern "C" int hd_accel_last_ms(const hd_plan* p, float* ms_powers, float* ms_sums)
+{
+    if (!p) return fail(nullptr, HD_E_INVAL, "hd_accel_last_ms: NULL plan");
+    if (p->ctx->acc_owner != p) return fail(p->ctx, HD_E_STATE, "hd_accel_last_ms: no search of this plan");
+    if (ms_powers) *ms_powers = p->ctx->acc_ms[0];
+    if (ms_sums) *ms_sums = p->ctx->acc_ms[1];
     return HD_OK;
 }
 

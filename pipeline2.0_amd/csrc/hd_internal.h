@@ -266,6 +266,18 @@ hipError_t fft_prepare(FftState* s, int64_t xstride, int64_t n, int ndm);
 hipError_t fft_series(FftState* s, const float* x, int64_t xstride, int64_t n, int ndm, hipStream_t st);
 hipError_t fft_zap(FftState* s, const int32_t* rng4, int nr, hipStream_t st);
 hipError_t fft_rednoise(FftState* s, const int32_t* boff, const double* cen, int nblk, hipStream_t st);
+// zero-acceleration harmonic-sum search of a plan's spectra (hd_accel.hip): the half-bin power
+// plane P [ndm][pstride] from the spectra, then the hits of stages 1 .. 2^(nstage-1) over
+// r2 in [r2lo, r2hi] (half bins); host side: taps, thresholds, significances, the merge
+hipError_t launch_acc_powers(const float2* F, int64_t fstride, int64_t nb, int ndm, const float* taps16, float* P,
+                             int64_t pstride, hipStream_t st);
+hipError_t launch_acc_harm(const float* P, int64_t pstride, int ndm, int64_t r2lo, int64_t r2hi, int nstage,
+                           const float* cut5, hd_acc_hit* hits, unsigned long long* count, int64_t cap, hipStream_t st);
+void accel_taps(float* taps16);
+double accel_powcut(double sigma, int H, double numindep);
+double accel_sigma(double power, int H, double numindep);
+int64_t accel_prune(hd_acc_hit* hits, int64_t n, double closest_r);
+void accel_sort(hd_acc_hit* hits, int64_t n);
 constexpr int64_t kRawTPad = 65536;   // zero rows after N in each channel-major raw row
 hipError_t launch_raw_transpose(const uint8_t* raw, int64_t N, int32_t nchan, int nbits, int nibble_hi_first,
                                 uint8_t* rawT, int64_t tstride, hipStream_t st);

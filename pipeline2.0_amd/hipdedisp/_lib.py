@@ -49,6 +49,8 @@ EXPORTED = [
     "hd_bary_diffbins", "hd_plan_set_bary", "hd_plan_data_end", "hd_run_dedisp_multi", "hd_plan_launch_passes", "hd_sp_prune",
     "hd_prefetch_raw_file", "hd_prefetch_raw_file_band", "hd_prefetch_fill", "hd_swap_raw",
     "hd_plan_extents", "hd_debug_fault",
+    "hd_set_fft", "hd_accel_taps", "hd_accel_powcut", "hd_accel_sigma", "hd_accel_search", "hd_accel_get_powers",
+    "hd_accel_last_ms", "hd_accel_prune",
 ]
 
 
@@ -82,6 +84,11 @@ class hd_extent(ctypes.Structure):
 
 
 _NPSR = 8
+
+
+class hd_acc_hit(ctypes.Structure):
+    _fields_ = [("dm", ctypes.c_int32), ("numharm", ctypes.c_int32), ("r2", ctypes.c_int32),
+                ("power", ctypes.c_float), ("sigma", ctypes.c_double)]
 
 
 class hd_rows_src(ctypes.Structure):
@@ -190,6 +197,15 @@ def load():
                                               P(ctypes.c_int32)]),
         "hd_rednoise": (ctypes.c_int, [vp, i32, i32, ctypes.c_double, ctypes.c_double]),
         "hd_get_fft": (ctypes.c_int, [vp, i32, i32, f32p]),
+        "hd_set_fft": (ctypes.c_int, [vp, i32, i32, f32p]),
+        "hd_accel_taps": (ctypes.c_int, [f32p]),
+        "hd_accel_powcut": (ctypes.c_int, [ctypes.c_double, i32, ctypes.c_double, P(ctypes.c_double)]),
+        "hd_accel_sigma": (ctypes.c_int, [ctypes.c_double, i32, ctypes.c_double, P(ctypes.c_double)]),
+        "hd_accel_search": (ctypes.c_int, [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, ctypes.c_double,
+                                           vp, i64, P(i64), P(ctypes.c_double)]),
+        "hd_accel_get_powers": (ctypes.c_int, [vp, i32, i64, i64, f32p]),
+        "hd_accel_last_ms": (ctypes.c_int, [vp, f32p, f32p]),
+        "hd_accel_prune": (ctypes.c_int, [vp, i64, ctypes.c_double, P(i64)]),
         "hd_bary_diffbins": (ctypes.c_int, [P(ctypes.c_double), P(ctypes.c_double), i32, ctypes.c_double,
                                             ctypes.c_double, P(ctypes.c_int32), i32, P(ctypes.c_int32)]),
         "hd_plan_set_bary": (ctypes.c_int, [vp, P(ctypes.c_int32), i32]),

@@ -78,6 +78,7 @@ class DedispJob:
         self.dedispersing_time = 0.0
         self.singlepulse_time = 0.0     # :539-546 on device (run_pass(single_pulse=...))
         self.FFT_time = 0.0             # :548-558 on device (run_pass(fft=...))
+        self.lo_accelsearch_time = 0.0  # :560-568 on device (run_pass(accel=...))
         self.ddplans = P.ddplans_for(self.backend)
         self.tempdir = tempfile.mkdtemp(suffix="_tmp", prefix=self.basefilenm,
                                         dir=tmpdir_base or ("/dev/shm" if os.path.isdir("/dev/shm") else None))
@@ -215,16 +216,26 @@ def _fft(job, plan, ddplan, passnum, tempdir, fft):
     fft_pass(job, plan, ddplan, passnum, tempdir, fft)
 
 
-def run_pass(job, ddplan, passnum, maskfilenm, tempdir, single_pulse=None, fft=None):
+def _accel(job, plan, ddplan, passnum, tempdir, accel):
+    """:560-568 (accelsearch -zmax 0) for the pass's DMs on the spectra the FFT stage left on the
+    device (hipdedisp.accel_stage); adds to job.lo_accelsearch_time."""
+    from .accel_stage import accel_pass
+    accel_pass(job, plan, ddplan, passnum, tempdir, accel)
+
+
+def run_pass(job, ddplan, passnum, maskfilenm, tempdir, single_pulse=None, fft=None, accel=None):
     """PALFA2_presto_search.py:498-529 for one pass: subbands (stage 1) then the DM sweep
     (stage 2); writes <tempdir>/<base>_DM<dm>.dat/.inf; returns (t_sub, t_dd).  Without
     subbands (:522-529) the reference makes one prepsubband call, timed as dedispersing
     time only: t_sub is 0 and the whole pass goes to t_dd.  single_pulse (a dict of
     maxwidth / threshold / workdir, config.searching's singlepulse_*) also runs :539-546 on
     the series while they are in HBM; fft (a dict of zaplist / baryv / write) then runs
-    :548-558 on them."""
+    :548-558 on them; accel (a dict of numharm / sigma / flo / fhi, config.searching's lo_accel_*;
+    needs fft) then runs the zero-acceleration search of :560-568 on those spectra."""
+    if accel is not None and fft is None:
+        raise PrestoError("run_pass: accel needs fft (the search reads the spectra the FFT stage leaves)")
     if not job.use_subbands:
-        return _run_pass_nosub(job, ddplan, passnum, maskfilenm, tempdir, single_pulse, fft)
+        return _run_pass_nosub(job, ddplan, passnum, maskfilenm, tempdir, single_pulse, fft, accel)
     subbasenm = "%s_DM%s" % (job.basefilenm, ddplan.subdmlist[passnum])
     eng = job.open_engine()
     job.load_mask(maskfilenm)
@@ -258,6 +269,8 @@ def run_pass(job, ddplan, passnum, maskfilenm, tempdir, single_pulse=None, fft=N
             _single_pulse(job, plan, ddplan, passnum, tempdir, single_pulse)
         if fft is not None:
             _fft(job, plan, ddplan, passnum, tempdir, fft)
+        if accel is not None:
+            _accel(job, plan, ddplan, passnum, tempdir, accel)
     finally:
         plan.destroy()
     job.subbanding_time += t_sub
@@ -265,7 +278,7 @@ def run_pass(job, ddplan, passnum, maskfilenm, tempdir, single_pulse=None, fft=N
     return t_sub, t_dd
 
 
-def _run_pass_nosub(job, ddplan, passnum, maskfilenm, tempdir, single_pulse=None, fft=None):
+def _run_pass_nosub(job, ddplan, passnum, maskfilenm, tempdir, single_pulse=None, fft=None, accel=None):
     """PALFA2_presto_search.py:522-529: `prepsubband -mask M -lodm -dmstep -numdms -downsamp
     (dd*sub) -numout N` straight on the raw data: channels (downsampled, float32) are the
     subbands of a nsub = nchan pass."""
@@ -285,6 +298,8 @@ def _run_pass_nosub(job, ddplan, passnum, maskfilenm, tempdir, single_pulse=None
             _single_pulse(job, plan, ddplan, passnum, tempdir, single_pulse)
         if fft is not None:
             _fft(job, plan, ddplan, passnum, tempdir, fft)
+        if accel is not None:
+            _accel(job, plan, ddplan, passnum, tempdir, accel)
     finally:
         plan.destroy()
     job.dedispersing_time += t_dd
@@ -307,7 +322,7 @@ def prepare_fft(job):
             p.destroy()
 
 
-def dedisperse_job(job, maskfilenm=None, per_dm=None, remove_dat=False, single_pulse=None, fft=None):
+def dedisperse_job(job, maskfilenm=None, per_dm=None, remove_dat=False, single_pulse=None, fft=None, accel=None):
     """The loop of PALFA2_presto_search.py:494-537: every pass of every DDplan stage (with
     the device single-pulse search of :539-546 when single_pulse is given), then
     `per_dm(job, dmstr, basenm)` for each new DM (the reference's downstream tools)."""
@@ -316,7 +331,7 @@ def dedisperse_job(job, maskfilenm=None, per_dm=None, remove_dat=False, single_p
     dmstrs = []
     for ddplan in job.ddplans:
         for passnum in range(ddplan.numpasses):
-            run_pass(job, ddplan, passnum, maskfilenm, job.tempdir, single_pulse, fft)
+            run_pass(job, ddplan, passnum, maskfilenm, job.tempdir, single_pulse, fft, accel)
             for dmstr in ddplan.dmlist[passnum]:
                 dmstrs.append(dmstr)
                 basenm = os.path.join(job.tempdir, job.basefilenm + "_DM" + dmstr)
